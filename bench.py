@@ -42,6 +42,7 @@ that is "f16s", the mode that meets the 1e-3 log-prob bar).  What the line carri
                    (`exchange_fallback`), what the start-up checks measured, the all-reduce's stand-alone cost.
 
   python bench.py --config original-sd      # BASELINE.json configs[0] on the GPU: B=4 state descriptions (per-layer fp32 kernels)
+  python bench.py --dump-outputs DIR        # also write the last timed step's loss, parameters, gradients and buffers as DIR/*.npy
   RN_BENCH_ONE_RANK_EXCHANGE=1 python bench.py    # diagnostic: the N > 1 code path (process group over RCCL, in-graph exchange, `comm`)
                                                   # on a ONE-rank communicator -- what a one-GPU box can execute of it"""
 import argparse
@@ -406,6 +407,32 @@ def timed_steps(step, steps, warmup, sync):
     return time.perf_counter() - t0, last
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, model, loss):
+    """--dump-outputs: what the timed path handed its caller after its LAST step, as DIR/<name>.npy -- the step's loss
+    (`loss.npy`), every parameter after the optimiser update (`param.<name>.npy`), every gradient the step left in
+    p.grad (`grad.<name>.npy`) and every buffer it updates (`buffer.<name>.npy`: BatchNorm statistics, the dropout draw
+    counter).  Floating tensors as float32, integer ones as float64.  Inputs and weights are seeded, so two builds run
+    with the same arguments can be compared file by file.  Sizes depend on the config only (2.1 M parameters at most)."""
+    import numpy as np
+    arrays = {"loss": loss.detach().float().cpu().numpy().reshape(-1)}
+    for name, p in model.named_parameters():
+        arrays["param." + name] = p.detach().float().cpu().numpy()
+        if p.grad is not None:
+            arrays["grad." + name] = p.grad.detach().float().cpu().numpy()
+    for name, b in model.named_buffers():
+        arrays["buffer." + name] = b.detach().cpu().numpy().astype(np.float32 if b.is_floating_point() else np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return total
+
+
 def max_over_ranks(dt, world, device):
     """The job's time is the slowest rank's."""
     import torch.distributed as dist
@@ -477,7 +504,12 @@ def main():
                          "both loss curves + held-out accuracy as `convergence` (train.convergence_run; ~15 s per mode at 300 steps)")
     ap.add_argument("--sustain", type=float, default=3.0,
                     help="seconds of back-to-back steps AFTER the timed K steps, same graph: reported as `sustained` (0: skip)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (loss, updated parameters, gradients, buffers) "
+                         "as DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch.distributed as dist
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -581,6 +613,9 @@ def main():
     H.TIMER.enabled = False
     with wd.guard("bench: warm-up + timed region (%d + %d steps)" % (args.warmup, args.steps), wd_s):
         dt, loss = timed_steps(lambda: trainer.step(img, qst, lab), args.steps, args.warmup, sync)
+    if args.dump_outputs and rank == 0:
+        # now, before any further step overwrites the graph's loss tensor and moves the weights on
+        dump_outputs(args.dump_outputs, model, loss)
     with_copy = None
     if use_graph and img0 is not img:
         # (both forms once more, back to back: the K timed steps above start 5 replays after an idle chip and run a few percent under

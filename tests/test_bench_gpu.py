@@ -59,3 +59,26 @@ def test_state_description_config_runs_with_both_cpu_baselines():
     c = d["cpu_baseline"]
     assert c["kind"] == "port" and c["value"] > 0 and "original-sd" in c["sample"] and "B=4" in c["sample"] and "cpu_baseline_sd4" not in d
     assert d["roofline"]["peak"] == 157.3 and "pair_build_k1" not in d
+
+
+def test_dump_outputs_repeat_with_the_same_arguments(tmp_path):
+    """--dump-outputs: the last timed step's loss, updated parameters, gradients and buffers as .npy files, float32 / float64, within
+    64 MB; two runs with the same arguments start from the same seeded inputs and weights, so they dump the same arrays (to the
+    run-to-run noise of the fp32 kernels' reductions).  --steps sets the timed step count that `ms_per_step` divides by."""
+    import numpy as np
+    import gold
+    runs = []
+    for i in range(2):
+        out = tmp_path / ("run%d" % i)
+        d = _bench("--config", "original-sd", "--steps", "3", "--no-cpu-baseline", "--no-parity", "--no-kernel-timing",
+                   "--dump-outputs", str(out))
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) < 1e-6 * d["value"]
+        files = sorted(os.listdir(str(out)))
+        arrays = {f[:-4]: np.load(str(out / f)) for f in files}
+        assert all(f.endswith(".npy") for f in files) and sum(a.nbytes for a in arrays.values()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+        assert "loss" in arrays and arrays["loss"].shape == (1,) and any(k.startswith("grad.") for k in arrays)
+        runs.append(arrays)
+    assert sorted(runs[0]) == sorted(runs[1])
+    for k in runs[0]:
+        assert runs[0][k].shape == runs[1][k].shape and gold.rel_err(runs[1][k], runs[0][k]) <= 1e-5, k

@@ -287,3 +287,29 @@ def test_reducing_chain_schedule_covers_every_tile_and_record_once(pkg, B, n, tp
         assert per_question_extra.max() == per_question_extra.min()
     else:
         assert per_question_extra.max() - per_question_extra.min() <= tpu - 1
+
+
+def test_bench_dump_outputs_files_types_and_size(tmp_path):
+    """bench.py --dump-outputs writes the step's loss, every parameter, every gradient and every buffer as float32 / float64 .npy
+    files; the largest config stays inside the 64 MB budget."""
+    import bench
+    import relationnetworks_clevr_amd as p
+    hyps = json.load(open(os.path.join(ROOT, "relationnetworks-clevr_amd", "config.json")))["hyperparams"]
+    for cfg in ("original-fp", "original-sd"):
+        m = bench.quiet_rn(p, dict(hyps[cfg], precision="auto"))
+        for q in m.parameters():
+            q.grad = torch.full_like(q, 0.5)
+        out = tmp_path / cfg
+        total = bench.dump_outputs(str(out), m, torch.tensor(1.25))
+        names = sorted(f[:-4] for f in os.listdir(str(out)))
+        want = sorted(["loss"] + ["param." + n for n, _ in m.named_parameters()] + ["grad." + n for n, _ in m.named_parameters()]
+                      + ["buffer." + n for n, _ in m.named_buffers()])
+        assert names == want and total <= 64 << 20
+        assert np.load(str(out / "loss.npy")).tolist() == [1.25]
+        for n_, q in m.named_parameters():
+            a = np.load(str(out / ("param." + n_ + ".npy")))
+            assert a.dtype == np.float32 and np.array_equal(a, q.detach().numpy())
+            assert np.all(np.load(str(out / ("grad." + n_ + ".npy"))) == 0.5)
+        for n_, b in m.named_buffers():
+            a = np.load(str(out / ("buffer." + n_ + ".npy")))
+            assert a.dtype == (np.float32 if b.is_floating_point() else np.float64) and np.array_equal(a, b.numpy())
