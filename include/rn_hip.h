@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define RN_ABI_VERSION 9   /* bumped whenever a signature or a buffer layout of this header changes */
+#define RN_ABI_VERSION 10  /* bumped whenever a signature or a buffer layout of this header changes */
 
 enum { RN_BF16 = 0, RN_F32 = 1, RN_F16 = 2, RN_FP8 = 3, RN_F32X3 = 4 };   /* RN_F16: pair matrix / split weights of the f16s forward only;
                                                              * RN_FP8: OCP e4m3 copies of the stored activations (h_dtype / a_dtype) */
@@ -104,7 +104,7 @@ int rn_g_linear_fwd(const void* A, int lda, const void* Wp, int ldw, const float
                     int dtype, int M, int N, int K, void* stream);
 
 /* Register-resident chains (rn_chain_rr.hip): the headline shape family -- L == 4, G == 256, at most 32 features per object,
- * question injected at layer 0 or 2.  8 waves x 32 pair rows per workgroup; the activation stays in MFMA operand registers from
+ * question injected at any layer 0..3.  8 waves x 32 pair rows per workgroup; the activation stays in MFMA operand registers from
  * layer to layer, LDS carries only the weight stream.  The forward chain is rn_g_chain_fwd_rr_f16s_alg0 (declared with the tables
  * of the factored first layer, below); what it leaves for the backward pass:
  *   H[0..2]: copies of the activations as ROW-BLOCKED images (see rn_g_wgrad_blocked, their only reader), e4m3 or bf16;
@@ -112,7 +112,7 @@ int rn_g_linear_fwd(const void* A, int lda, const void* Wp, int ldw, const float
  *            element of layer l as 64-bit LANE masks in the kernel's own accumulator layout (opaque; the consumers are
  *            rn_g_chain_bwd_rr* and rn_fp8_copy_health);
  *   xg_part: fp32 sums of the UN-rounded last activation, one row per 256-row tile.
- * rn_g_chain_rr_tile() = 256: the tile height (M and, with the question at layer 2, n*n must be multiples of it). */
+ * rn_g_chain_rr_tile() = 256: the tile height (M and, with the question at layer 1..3, n*n must be multiples of it). */
 int rn_g_chain_rr_tile(void);
 
 /* Backward (pair-sum broadcast + ReLU gates + the three dgrad steps):
@@ -237,9 +237,14 @@ int rn_g_wgrad_blocked(const void* const* dZ, const int* dz_dtype, const void* c
  * positive elements whose byte is 0 (flushed), bytes at the clamp 0x7e, largest byte.  The caller decides what to do about a
  * flushed fraction that is too large (dp.DataParallelTrainer switches to 16-bit copies). */
 int rn_fp8_copy_health(const void* mask, const void* img, unsigned long long* out4, int M, void* stream);
-/* Rq[b, f] (B, 256) fp32 = sum over the rows of question b of a 16-bit row-blocked image -- the per-question sums of dZ when
- * the splits above straddle questions.  rows_per_question % 8 == 0. */
-int rn_blocked_question_sums(const void* img, float* Rq, int M, int rows_per_question, void* stream);
+/* Rq[b, f] (B, 256) fp32 = per-question column sums of the injected layer's gradient, from exactly one of:
+ *   img (mask NULL): a 16-bit row-blocked image, summed over the rows of question b -- the per-question sums of a stored dZ when
+ *     the splits above straddle questions.  rows_per_question % 8 == 0; dxg not read.
+ *   mask (img NULL): the forward chain's layer-3 lane masks (mask[3] of rn_g_chain_fwd_rr_f16s_alg0, M * 32 bytes, 16-byte aligned):
+ *     C[b, f] = #{pair rows m of question b with H_3[m, f] > 0} (exact integers in fp32), or dxg[b, f] * C[b, f] with the (B, 256)
+ *     fp32 dxg given -- the sums of the last layer's gradient dZ_3 = gate_3 x dxg[question], which the e4m3 training set never
+ *     stores (the question injected at layer 3).  rows_per_question % 32 == 0.  Reads 32 bytes per pair row. */
+int rn_blocked_question_sums(const void* img, const void* mask, const float* dxg, float* Rq, int M, int rows_per_question, void* stream);
 
 /* Backward of the pair expansion, algebraic form: reduce the gradient
  * of a g layer's pre-activation over the pair axes instead of materialising dP:
@@ -474,10 +479,12 @@ int rn_bn_relu_bwd_conv_wgrad(const float* dy, const float* xc, const float* inp
  *                fp16(W_l), Wlo[l] = fp16(W_l - hi) (modes 4 / 8).  Nothing depends on the tile index: a question's outputs are
  *                the same wherever it sits in the batch and for any order of its objects, up to fp32 summation order (~1e-6).
  *                What the module's eval() runs (options.eval_two_pass).  Twice the MFMAs of layers 1..3.
- *   inject_layer = 0: the question is part of the tables (Q > 0 in rn_pair_tables).  inject_layer = 2 (the "IR" variants,
- *     model.py:131-142; tables built with Q = 0): layer 2's input is [H_1 | q[b]], i.e. W_2 [H_1 | q] + b_2 = W_2[:, 0:256] H_1 + Vq[b]
- *     with Vq (B, 256) fp32 = W_2[:, 256:] q[b] + b_2 prepared by the caller (one small rn_gemm_f32); Whi[2] holds W_2[:, 0:256]
- *     only, bias[2] is ignored.  Needs n divisible by 32 and n*n by 256.
+ *   inject_layer = 0: the question is part of the tables (Q > 0 in rn_pair_tables).  inject_layer = l in 1..3 (l = 2: the "IR"
+ *     variants, model.py:131-142; the reference's --question-injection moves it; tables built with Q = 0): layer l's input is
+ *     [H_{l-1} | q[b]], i.e. W_l [H_{l-1} | q] + b_l = W_l[:, 0:256] H_{l-1} + Vq[b] with Vq (B, 256) fp32 = W_l[:, 256:] q[b] + b_l
+ *     prepared by the caller (one small rn_gemm_f32); Whi[l] holds W_l[:, 0:256] only, bias[l] is ignored.  Needs n divisible by
+ *     32 and n*n by 256.  With l = 3 the last layer's gradient is never stored (e4m3 set): its per-question sums are dxg x the gate
+ *     counts of mask[3] (rn_blocked_question_sums, mask form).
  *   H / mask: both NULL (inference) or H[0..2] (H[3] NULL) + the four masks (training).  h_dtype: the type of the stored H_0..2 rows
  *     -- RN_BF16 (M x 256 bf16) or RN_FP8 (M x 256 e4m3 bytes, value = byte value), both as ROW-BLOCKED images (the only reader is
  *     rn_g_wgrad_blocked).  Ignored when H is NULL.

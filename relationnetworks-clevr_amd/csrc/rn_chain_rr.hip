@@ -372,6 +372,10 @@ struct F16Vm {
   static constexpr int PF_PER = (NK0 + 7) / 8;
   static constexpr int VC_STAGE = (RR_L - 1) * 8 + 4;                // ALG0: the stage that requests the next tile's bias row
   static constexpr int VQ_STAGE = (RR_L - 1) * 8 + 2;                // INJ: ... and the next tile's question row of layer INJ
+  // INJ = 1, 3 with 16-bit copies: the row is a plain load in the tail's source (the compiler waits for it and may hoist it into the
+  // last stage); not counted by ops / tail, an uncounted request only makes the hand-counted waits over-wait.  Carried in registers
+  // from VQ_STAGE instead, it spills two VGPRs in that variant (as the INJ = 2 one does, left as it is)
+  static constexpr bool VQ_TAIL = (INJ == 1 || INJ == 3) && STORE && !H8;
   // Only the fragments a stage's MFMAs read are requested: layer 0 multiplies NK0 of a block's 16 fragments (hi and lo), the
   // one-pass layers the hi image only (each 1-KB request costs ~100 issue cycles beside the MFMAs: streaming whole 32-KB
   // stages measured 32 of the kernel's 173 us).
@@ -386,7 +390,7 @@ struct F16Vm {
     if ((sidx >> 3) == RR_L - 1)
       for (int c = 0; c < PF_PER; ++c) k += ((sidx & 7) * PF_PER + c < NK0) ? 1 : 0;
     if (ALG0 && sidx == VC_STAGE) k += 1;
-    if (INJ > 0 && sidx == VQ_STAGE) k += 1;
+    if (INJ > 0 && !VQ_TAIL && sidx == VQ_STAGE) k += 1;
     if (GATE && (sidx >> 3) == RR_L - 1 && (sidx & 7) >= 1) k += 1;   // the H_2 | gate cells of block (sidx & 7) - 1
     return k;
   }
@@ -410,7 +414,13 @@ struct F16Vm {
 // INJ > 0 -- the question injected at layer INJ (the reference's "IR" variants, model.py:131-142): the layer's input is
 //   [H_{INJ-1} | q[b]], so W_INJ [H | q] + b = W_INJ[:, 0:256] H + (W_INJ[:, 256:] q[b] + b): the bracket is a per-QUESTION constant
 //   -- Vq[b][256], fp32, one small product on the host side -- and takes the place of the layer's bias row in LDS for the tile (a
-//   256-row tile lies inside one question: n*n % 256 == 0).  The next tile's row is fetched during the last layer.
+//   256-row tile lies inside one question: n*n % 256 == 0).  The next tile's row is fetched during the last layer (VQ_STAGE) and
+//   wave 0 writes it into the layer's bias slot at the very end of the tile, followed by its lgkmcnt(0): every later read of the
+//   slot sits behind at least the barrier of the next tile's stage (0, 0) -- INJ = 1 reads it first at stage (1, 0), 9 barriers on.
+//   INJ = 3 (the un-swapped last layer): the row is read as b3, per output block at the head of the NEXT stage and for block 7 at the
+//   head of the tile tail -- the only reads not separated from wave 0's write by a stage barrier.  The XG + ALG0 tail closes with a
+//   barrier in front of that write (the eight waves' pair-sum rows meet in LDS), and every wave's xs, hence its b3 read, is
+//   complete before it: the slot is free when wave 0 overwrites it.  (Without that barrier INJ = 3 would race: static_assert.)
 // Passes.  Layer 0 runs hi + lo (its K = 64 / 192 product is a twelfth .. a quarter of a later layer's).  Layers 1..3 run ONE pass
 // on TILE-DITHERED hi images (rn_pack_matrix_frag_many): tile t multiplies image t mod V, V = 4 roundings of the weights whose
 // mean is within ulp / 8 of the fp32 weight.  What keeps single-pass 16-bit arithmetic at 3e-3 of the fp32 reference is not the
@@ -452,7 +462,8 @@ __global__ __launch_bounds__(RR_NT) void g_chain_rr_f16s_kernel(const f16* __res
                                                                 const float* __restrict__ Vq = nullptr, int rows_per_b = 1,
                                                                 int njp = 0, int n_zero = 0) {
   static_assert(!RAG || (ALG0 && INJ == 0 && XG), "padded j axis: the factored first layer with the question at layer 0");
-  static_assert(INJ >= 0 && INJ < RR_L - 1, "the injected layer is one of the swapped-operand layers");
+  static_assert(INJ >= 0 && INJ < RR_L, "the question is injected at one of the four layers");
+  static_assert(INJ < RR_L - 1 || (XG && ALG0), "the last layer's question row is overwritten behind the pair-sum barrier of the tail");
   static_assert(!H8 || STORE, "e4m3 copies of H_0..2 (a stored H_3 stays bf16: the pair sum reads it)");
   static_assert(!GATE || (H8 && MASK && !ST3), "the gate image belongs to the training output set with e4m3 copies");
   static_assert(!LO || (!STORE && !MASK), "two passes on every layer: the inference variant");
@@ -804,7 +815,7 @@ __global__ __launch_bounds__(RR_NT) void g_chain_rr_f16s_kernel(const f16* __res
             if (i < NK0) out[i] = in_frag(m0n, i);
           }
           if (ALG0 && sidx == Vm::VC_STAGE && c == 1) vcreg = vc_load(m0n);
-          if (INJ > 0 && sidx == Vm::VQ_STAGE && c == 1) vqreg = vq_load(tnext);
+          if (INJ > 0 && !Vm::VQ_TAIL && sidx == Vm::VQ_STAGE && c == 1) vqreg = vq_load(tnext);
           __builtin_amdgcn_sched_barrier(0);
         }
       }
@@ -892,6 +903,7 @@ __global__ __launch_bounds__(RR_NT) void g_chain_rr_f16s_kernel(const f16* __res
       if constexpr (ALG0) *reinterpret_cast<f32x4*>(vc_s + lane * 4) = vcreg;
       if constexpr (INJ > 0) {
         if (w == 0) {
+          if constexpr (Vm::VQ_TAIL) vqreg = vq_load(tnext);
           *reinterpret_cast<f32x4*>(bias_s + INJ * RR_G + lane * 4) = vqreg;
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         }
@@ -1315,7 +1327,7 @@ extern "C" int rn_g_chain_rr_tile(void) { return RR_TM; }
 size_t rnws_rr_mask(int M) { return M > 0 ? (size_t)M * 32 : 0; }
 
 static int rr_check_inject(const char* who, const float* Vq, int inj, int n) {
-  RN_CHECK_ARG(inj == 0 || inj == 2, "%s: the question can be injected at layer 0 (tables) or 2 (got %d)", who, inj);
+  RN_CHECK_ARG(inj >= 0 && inj < RR_L, "%s: the question can be injected at layer 0 (tables) or 1, 2, 3 (a per-question bias row; got %d)", who, inj);
   RN_CHECK_ARG(inj == 0 || (Vq && ((uintptr_t)Vq % 16 == 0)), "%s: injection at layer %d needs the 16-byte aligned question rows Vq", who, inj);
   RN_CHECK_ARG(inj == 0 || ((long)n * n) % RR_TM == 0, "%s: injection at layer %d needs n*n %% %d == 0 (n=%d)", who, inj, RR_TM, n);
   return 0;
@@ -1350,6 +1362,24 @@ static int rr_f16s_args(const char* who, RRArgsF& a, const void* const* Whi, con
   return 0;
 }
 
+// The five variants of a question injected at layer INJ > 0 (whole waves per (question, i): no padded j axis): two-pass
+// inference, one-pass inference, training with e4m3 copies + gate, with e4m3 copies, with 16-bit copies.
+template <int INJ>
+static void rr_launch_inj_at(bool two, int nh, bool h8, bool gate, int grid, hipStream_t s, const f16* Xp, const RRArgsF& a, float* xg_part,
+                             int ntiles, const float* Vc, int n, const float* Vq, int rpb) {
+  if (two) g_chain_rr_f16s_kernel<4, false, false, false, true, true, INJ, false, 0, false, false, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb);
+  else if (nh == 0) g_chain_rr_f16s_kernel<4, false, false, false, true, true, INJ><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb);
+  else if (h8 && gate) g_chain_rr_f16s_kernel<4, true, false, true, true, true, INJ, true, 0, false, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb);
+  else if (h8) g_chain_rr_f16s_kernel<4, true, false, true, true, true, INJ, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb);
+  else g_chain_rr_f16s_kernel<4, true, false, true, true, true, INJ><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb);
+}
+static void rr_launch_inj(int inj, bool two, int nh, bool h8, bool gate, int grid, hipStream_t s, const f16* Xp, const RRArgsF& a, float* xg_part,
+                          int ntiles, const float* Vc, int n, const float* Vq, int rpb) {
+  if (inj == 1) rr_launch_inj_at<1>(two, nh, h8, gate, grid, s, Xp, a, xg_part, ntiles, Vc, n, Vq, rpb);
+  else if (inj == 2) rr_launch_inj_at<2>(two, nh, h8, gate, grid, s, Xp, a, xg_part, ntiles, Vc, n, Vq, rpb);
+  else rr_launch_inj_at<3>(two, nh, h8, gate, grid, s, Xp, a, xg_part, ntiles, Vc, n, Vq, rpb);
+}
+
 // The forward chain (f16s arithmetic, factored first layer): Xp16 = fp16 object rows (B*n [+ 1], 64).
 extern "C" int rn_g_chain_fwd_rr_f16s_alg0(const void* Xp16, const float* Vc, int n, int njp, const void* const* Whi, const void* const* Wlo, int dither,
                                            const float* const* bias, void* const* H, int h_dtype, void* const* mask, int gate_in_h2,
@@ -1382,7 +1412,7 @@ extern "C" int rn_g_chain_fwd_rr_f16s_alg0(const void* Xp16, const float* Vc, in
   if (two) {
     const int nz = rag ? (M / (n * njp)) * n : 0;
     if (rag) g_chain_rr_f16s_kernel<4, false, false, false, true, true, 0, false, 0, true, false, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, nullptr, 1, njp, nz);
-    else if (inject_layer == 2) g_chain_rr_f16s_kernel<4, false, false, false, true, true, 2, false, 0, false, false, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb);
+    else if (inject_layer > 0) rr_launch_inj(inject_layer, true, 0, false, false, grid, s, Xp, a, xg_part, ntiles, Vc, n, Vq, rpb);
     else g_chain_rr_f16s_kernel<4, false, false, false, true, true, 0, false, 0, false, false, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n);
   } else if (rag) {
     const int nz = (M / (n * njp)) * n;                               // the all-zero object row behind the B * n real ones
@@ -1390,11 +1420,8 @@ extern "C" int rn_g_chain_fwd_rr_f16s_alg0(const void* Xp16, const float* Vc, in
     else if (h8 && gate) g_chain_rr_f16s_kernel<4, true, false, true, true, true, 0, true, 0, true, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, nullptr, 1, njp, nz);
     else if (h8) g_chain_rr_f16s_kernel<4, true, false, true, true, true, 0, true, 0, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, nullptr, 1, njp, nz);
     else g_chain_rr_f16s_kernel<4, true, false, true, true, true, 0, false, 0, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, nullptr, 1, njp, nz);
-  } else if (inject_layer == 2) {
-    if (nh == 0) g_chain_rr_f16s_kernel<4, false, false, false, true, true, 2><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb);
-    else if (h8 && gate) g_chain_rr_f16s_kernel<4, true, false, true, true, true, 2, true, 0, false, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb);
-    else if (h8) g_chain_rr_f16s_kernel<4, true, false, true, true, true, 2, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb);
-    else g_chain_rr_f16s_kernel<4, true, false, true, true, true, 2><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb);
+  } else if (inject_layer > 0) {
+    rr_launch_inj(inject_layer, false, nh, h8, gate, grid, s, Xp, a, xg_part, ntiles, Vc, n, Vq, rpb);
   } else {
     if (nh == 0) g_chain_rr_f16s_kernel<4, false, false, false, true, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n);
 #ifdef RN_DIAG

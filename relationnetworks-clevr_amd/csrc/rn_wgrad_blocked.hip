@@ -788,6 +788,47 @@ extern "C" int rn_relu_gate_image(const void* mask, void* img, int M, void* stre
   return 0;
 }
 
+// Per-question counts of the positive pre-activations of the LAST g layer (rn_blocked_question_sums with mask), from the forward
+// chain's layer-3 lane masks (layout as
+// rn_relu_gate_image reads it: a 32-row block's record holds, per 32-feature block, 32 dwords of 32 feature bits -- one dword per
+// row, in a row order that a count does not need to know).  out[b, f] = C[b, f] = #{rows of question b with gate_3 = 1}, or
+// dxg[b, f] * C[b, f] with dxg given: the column sums of the never-stored dZ_3 = gate_3 x dxg[question] (the question injected at
+// the last layer), exact up to the one product.  A workgroup = (question, 32-feature block); thread (fb, g) adds bit fb of dwords
+// 4 g .. 4 g + 3 of every row block of the question, the 8 g partial counts meet in LDS (integers: any order, same result).
+__global__ __launch_bounds__(256) void mask_question_counts_kernel(const unsigned* __restrict__ mask, const float* __restrict__ dxg,
+                                                                   float* __restrict__ out, int blocks_per_q) {
+  __shared__ unsigned red[8][32];
+  const int b = blockIdx.x >> 3, fblk = blockIdx.x & 7, fb = threadIdx.x & 31, g = threadIdx.x >> 5;
+  const u32x4* src = reinterpret_cast<const u32x4*>(mask + ((long)b * blocks_per_q * 8 + fblk) * 32 + 4 * g);
+  constexpr int QC_U = 8;                                 // row blocks in flight per thread (8 KB per workgroup)
+  unsigned cnt = 0;
+  int rb = 0;
+  for (; rb + QC_U <= blocks_per_q; rb += QC_U) {
+    u32x4 v[QC_U];
+#pragma unroll
+    for (int u = 0; u < QC_U; ++u) v[u] = src[(long)(rb + u) * 64];     // (a row block's record: 8 x 32 dwords = 64 u32x4)
+#pragma unroll
+    for (int u = 0; u < QC_U; ++u)
+#pragma unroll
+      for (int e = 0; e < 4; ++e) cnt += (v[u][e] >> fb) & 1u;
+  }
+  for (; rb < blocks_per_q; ++rb) {
+    const u32x4 v = src[(long)rb * 64];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) cnt += (v[e] >> fb) & 1u;
+  }
+  red[g][fb] = cnt;
+  __syncthreads();
+  if (g == 0) {
+    unsigned c = 0;
+#pragma unroll
+    for (int q = 0; q < 8; ++q) c += red[q][fb];
+    const long o = (long)b * 256 + fblk * 32 + fb;
+    out[o] = dxg ? dxg[o] * (float)c : (float)c;
+  }
+}
+
+
 // Health of an e4m3 activation copy (rn_fp8_copy_health): how much of a layer's post-ReLU activation does NOT survive as an e4m3
 // byte.  The copies use a fixed scale of 1 (rn_common.h): values below 2^-10 flush to zero, values above 448 are clamped.  The
 // forward chain's lane masks say which elements were positive BEFORE rounding (swapped layers 0..2: word 4 j + r of a block, lane
@@ -891,9 +932,18 @@ __global__ __launch_bounds__(256) void blocked_question_sums_kernel(const unsign
   if (ph == 0) Rq[(long)b * 256 + f] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
 
-extern "C" int rn_blocked_question_sums(const void* img, float* Rq, int M, int rows_per_question, void* stream) {
-  RN_CHECK_ARG(img && Rq && M > 0 && rows_per_question > 0 && rows_per_question % 8 == 0 && M % rows_per_question == 0,
-               "rn_blocked_question_sums: needs rows_per_question %% 8 == 0 dividing M (M=%d, rows_per_question=%d)", M, rows_per_question);
+// img != NULL: the column sums of a 16-bit row-blocked image; mask != NULL (img NULL): the last layer's gate counts C, or dxg x C
+extern "C" int rn_blocked_question_sums(const void* img, const void* mask, const float* dxg, float* Rq, int M, int rows_per_question, void* stream) {
+  RN_CHECK_ARG(Rq && (!img != !mask) && M > 0 && rows_per_question > 0 && M % rows_per_question == 0,
+               "rn_blocked_question_sums: needs Rq, exactly one of img / mask, rows_per_question dividing M (M=%d, rows_per_question=%d)", M, rows_per_question);
+  if (mask) {
+    RN_CHECK_ARG(rows_per_question % 32 == 0 && (uintptr_t)mask % 16 == 0,
+                 "rn_blocked_question_sums: lane masks need rows_per_question %% 32 == 0 and 16-byte alignment (rows_per_question=%d)", rows_per_question);
+    mask_question_counts_kernel<<<(M / rows_per_question) * 8, 256, 0, (hipStream_t)stream>>>((const unsigned*)mask, dxg, Rq, rows_per_question / 32);
+    RN_LAUNCH_CHECK("rn_blocked_question_sums");
+    return 0;
+  }
+  RN_CHECK_ARG(rows_per_question % 8 == 0, "rn_blocked_question_sums: needs rows_per_question %% 8 == 0 (rows_per_question=%d)", rows_per_question);
   blocked_question_sums_kernel<<<(M / rows_per_question) * 4, 256, 0, (hipStream_t)stream>>>((const unsigned char*)img, Rq, rows_per_question / 8);
   RN_LAUNCH_CHECK("rn_blocked_question_sums");
   return 0;

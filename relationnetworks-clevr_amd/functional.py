@@ -331,7 +331,7 @@ def chain_ok(plan: LayerPlan, B, n):
     resolves to) -- shared by the module, the autograd function and bench.py: exactly four 256-wide g layers, at most 32 features
     per object, and the question injected
       at layer 0 (config.json original-fp): any n % 4 == 0 (n % 32 != 0 runs on the padded j axis), whole 256-row tiles;
-      at layer 2 (ir-fp): whole waves per (question, i) and whole tiles per question (n % 32 == 0, n*n % 256 == 0).
+      at layer 1, 2 (ir-fp) or 3: whole waves per (question, i) and whole tiles per question (n % 32 == 0, n*n % 256 == 0).
     Everything else -- the 512-wide *-sd models, other depths, forward hooks -- runs the per-layer kernels (bf16 / fp32)."""
     if not (plan.L == 4 and all(w == 256 for w in plan.widths) and plan.k <= 32):
         return False
@@ -339,7 +339,8 @@ def chain_ok(plan: LayerPlan, B, n):
     if plan.inject == 0:
         njp = padded_j(n)
         return njp is not None and (B * n * njp) % T == 0
-    return plan.inject == 2 and plan.ktrue[2] == 256 + plan.Q and n % 32 == 0 and (n * n) % T == 0
+    inj = plan.inject
+    return 0 < inj < plan.L and plan.ktrue[inj] == 256 + plan.Q and n % 32 == 0 and (n * n) % T == 0
 
 
 f16s_ok = chain_ok
@@ -546,7 +547,7 @@ class RelationalFunction(torch.autograd.Function):
         need_grad = grad_on and any(ctx.needs_input_grad)      # under no_grad nothing is kept for a backward pass (inference kernels)
         if chain and not chain_ok(plan, B, n):
             raise RuntimeError('precision "f16s" needs the register-resident chains: four 256-wide g layers, <= 32 features per object, '
-                               'the question at layer 0 (n % 4 == 0) or 2 (n % 32 == 0), whole 256-row tiles (functional.chain_ok); '
+                               'the question at layer 0 (n % 4 == 0) or 1, 2, 3 (n % 32 == 0), whole 256-row tiles (functional.chain_ok); '
                                'use "auto", "bf16" or "fp32" here')
         if coord is not None and not chain:
             raise RuntimeError("internal: a coordinate table was passed but the chain path does not apply (grid_path_ok)")
@@ -794,6 +795,14 @@ class RelationalFunction(torch.autograd.Function):
             Rq2 = torch.empty(B, N, **f32)
             dq = torch.empty(B, Q, **f32)
 
+            def _question_sums(l):
+                if l == L - 1:
+                    # the last layer's gradient gate_3 x dxg[question] is not stored with e4m3 copies: Rq = dxg x (the per-question
+                    # counts of its gate), exact in fp32 -- the 16-bit copies take the same route
+                    H.mask_question_counts(masks[l], Rq2, M, n * n, dxg=dxg)
+                else:
+                    H.blocked_question_sums(dZ_of[l], Rq2, M, n * n)   # (this layer's dZ is a row-blocked image)
+
             def _wgrad_question(l=l, N=N, kt=kt):                   # gW[l][:, G_prev:] = Rq^T q  (bound NOW: N, kt are layer 0's further down)
                 H.gemm_f32(Rq2, 1, N, q, Q, 1, gW[l], kt, N, Q, B, c_off=kt - Q)
             if dq_by_event:
@@ -803,7 +812,7 @@ class RelationalFunction(torch.autograd.Function):
                 # the conv weight gradients behind the weight-gradient launch: no gain.)
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    H.blocked_question_sums(dZ_of[l], Rq2, M, n * n)
+                    _question_sums(l)
                     H.gemm_f32(Rq2, N, 1, wl, kt, 1, dq, Q, B, Q, N, b_off=kt - Q)
                     _GRAD_EVENTS.clear()
                     _GRAD_EVENTS[dq.data_ptr()] = (side.record_event(), None)
@@ -815,7 +824,7 @@ class RelationalFunction(torch.autograd.Function):
                         _wgrad_question()
                 keep.append([Rq2, q, wl, dq])
             else:
-                H.blocked_question_sums(dZ_of[l], Rq2, M, n * n)       # (this layer's dZ is a row-blocked image)
+                _question_sums(l)
                 H.gemm_f32(Rq2, N, 1, wl, kt, 1, dq, Q, B, Q, N, b_off=kt - Q)   # Rq @ W[:, -Q:]
             if dq_by_event:
                 pass

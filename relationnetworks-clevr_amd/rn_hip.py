@@ -16,7 +16,7 @@ LIB_PATH = os.path.join(_HERE, "librn_hip.so")
 _PRODUCT_LIB_PATH = LIB_PATH                         # (tools may point LIB_PATH at a variant build)
 RN_BF16, RN_F32, RN_F16, RN_FP8, RN_F32X3 = 0, 1, 2, 3, 4
 RN_RELU, RN_ACCUMULATE = 1, 2
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 _lib = None
 
@@ -48,7 +48,7 @@ SIGNATURES = {
     "rn_g_linear_bwd_wgrad": (_I, [_P, _I, _P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "rn_wgrad_blocked_splits": (_I, [_I, _I, _I, _I]),
     "rn_wgrad_blocked_db_partials_offset": (_Z, [_I, _I, _I, _I, _I]),
-    "rn_blocked_question_sums": (_I, [_P, _P, _I, _I, _P]),
+    "rn_blocked_question_sums": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "rn_g_wgrad_blocked": (_I, [_P, _P, _P, _I, _P, _I, _I, _P, _P, _I, _P, _I, _P]),
     "rn_fp8_copy_health": (_I, [_P, _P, _P, _I, _P]),
     "rn_pair_reduce_bwd": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
@@ -446,7 +446,23 @@ def wgrad_blocked_splits(M, rows_per_question=0, njobs=1, aligned=False):
 
 @_timed("pair_reduce")
 def blocked_question_sums(img, Rq, M, rows_per_question):
-    _check(load().rn_blocked_question_sums(img.data_ptr(), Rq.data_ptr(), M, rows_per_question, _stream()), "rn_blocked_question_sums")
+    _check(load().rn_blocked_question_sums(img.data_ptr(), None, None, Rq.data_ptr(), M, rows_per_question, _stream()), "rn_blocked_question_sums")
+
+
+@_timed("pair_reduce")
+def mask_question_counts(mask, out, M, rows_per_question, dxg=None):
+    """Per-question counts of the last g layer's positive pre-activations from its forward lane masks (M * 32 bytes; the mask form of
+    rn_blocked_question_sums):
+    out (B, 256) fp32 = C, or dxg * C with dxg given (the question sums of the never-stored last-layer gradient)."""
+    B = M // rows_per_question if rows_per_question > 0 else 0
+    if mask.dtype != torch.uint8 or mask.numel() < M * 32 or not mask.is_contiguous():
+        raise ValueError("mask_question_counts: mask must be a contiguous uint8 buffer of M * 32 bytes (M=%d, got %d)" % (M, mask.numel()))
+    if out.dtype != torch.float32 or tuple(out.shape) != (B, 256) or not out.is_contiguous():
+        raise ValueError("mask_question_counts: out must be a contiguous (%d, 256) fp32 tensor (got %s %s)" % (B, out.dtype, tuple(out.shape)))
+    if dxg is not None and (dxg.dtype != torch.float32 or tuple(dxg.shape) != (B, 256) or not dxg.is_contiguous()):
+        raise ValueError("mask_question_counts: dxg must be a contiguous (%d, 256) fp32 tensor (got %s %s)" % (B, dxg.dtype, tuple(dxg.shape)))
+    _check(load().rn_blocked_question_sums(None, mask.data_ptr(), _ptr(dxg), out.data_ptr(), M, rows_per_question, _stream()), "rn_blocked_question_sums")
+    return out
 
 
 def rows_to_blocked(src, back=False):
