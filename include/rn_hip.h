@@ -483,7 +483,7 @@ int rn_bn_relu_bwd_conv_wgrad(const float* dy, const float* xc, const float* inp
  *     variants, model.py:131-142; the reference's --question-injection moves it; tables built with Q = 0): layer l's input is
  *     [H_{l-1} | q[b]], i.e. W_l [H_{l-1} | q] + b_l = W_l[:, 0:256] H_{l-1} + Vq[b] with Vq (B, 256) fp32 = W_l[:, 256:] q[b] + b_l
  *     prepared by the caller (one small rn_gemm_f32); Whi[l] holds W_l[:, 0:256] only, bias[l] is ignored.  Needs n divisible by
- *     32 and n*n by 256.  With l = 3 the last layer's gradient is never stored (e4m3 set): its per-question sums are dxg x the gate
+ *     32 and n*n by 256, or (l = 2 only) the padded j axis below.  With l = 3 the last layer's gradient is never stored (e4m3 set): its per-question sums are dxg x the gate
  *     counts of mask[3] (rn_blocked_question_sums, mask form).
  *   H / mask: both NULL (inference) or H[0..2] (H[3] NULL) + the four masks (training).  h_dtype: the type of the stored H_0..2 rows
  *     -- RN_BF16 (M x 256 bf16) or RN_FP8 (M x 256 e4m3 bytes, value = byte value), both as ROW-BLOCKED images (the only reader is
@@ -497,7 +497,7 @@ int rn_bn_relu_bwd_conv_wgrad(const float* dy, const float* xc, const float* inp
  *     H / mask cover the M padded rows, and xg_part holds TWO partial rows per 256-row tile, (M / 256 * 2, 256) -- reduce with
  *     rn_pair_sum_tiles.  The backward side (rn_g_chain_bwd_rr with rows_per_question = n * njp, rn_g_wgrad_blocked,
  *     rn_pair_reduce_bwd with njp) then sees zero gradients for the invalid rows without knowing about the padding.  Question at
- *     layer 0 only.
+ *     layer 0 or 2 (a tile that straddles two questions reads each wave's own row of Vq).
  *   gate_in_h2 (with the e4m3 training output set only): != 0 -- the last layer's ReLU gate (= mask[3]) is also written into the
  *     sign bits of the H[2] image: byte (m, f) = e4m3(H_2[m, f]) | gate_3[m, f] << 7 (exactly what rn_relu_gate_image of
  *     include/rn_hip_debug.h merges into a plain image).  That one image is both operands of the last layer's gate job in

@@ -421,6 +421,10 @@ struct F16Vm {
 //   head of the tile tail -- the only reads not separated from wave 0's write by a stage barrier.  The XG + ALG0 tail closes with a
 //   barrier in front of that write (the eight waves' pair-sum rows meet in LDS), and every wave's xs, hence its b3 read, is
 //   complete before it: the slot is free when wave 0 overwrites it.  (Without that barrier INJ = 3 would race: static_assert.)
+//   RAG (instantiated for INJ = 2): rows per question n * njp are a multiple of 128 only, so a tile may hold two questions, split
+//   at a wave boundary.  The second question's row lives in the layer-0 bias slot (ALG0: layer 0 reads vc_s, never that slot);
+//   wave 1 fetches the row of the next tile's LAST question with the same vq_load and writes it there beside wave 0's write, so the
+//   ordering argument above holds for both rows.  Each wave picks its slot per tile (inj_off: one SGPR).
 // Passes.  Layer 0 runs hi + lo (its K = 64 / 192 product is a twelfth .. a quarter of a later layer's).  Layers 1..3 run ONE pass
 // on TILE-DITHERED hi images (rn_pack_matrix_frag_many): tile t multiplies image t mod V, V = 4 roundings of the weights whose
 // mean is within ulp / 8 of the fp32 weight.  What keeps single-pass 16-bit arithmetic at 3e-3 of the fp32 reference is not the
@@ -435,7 +439,7 @@ struct F16Vm {
 // ABL (RN_DIAG builds only: timing ablations, WRONG results) -- 1: no bias rows (the block's first MFMA starts from zero), 2: no
 // barriers, 4: no waits for the weight stream, 8: no copy-out (no staging reads, no H stores), 16: no mask stores, 32: no epilogue
 // at all, 64: no weight requests
-// RAG (ALG0, question at layer 0) -- object counts that are no multiple of 32 (the 14 x 14 grid: n = 196): the j axis of every
+// RAG (ALG0, question at layer 0 or as a per-question row) -- object counts that are no multiple of 32 (the 14 x 14 grid: n = 196): the j axis of every
 // (question, i) group is PADDED to njp = 32 ceil(n / 32) pair rows, so that a wave still lies inside one group (one Vc bias
 // row) and the factored first layer applies -- no 443-MB pair matrix, K = 64 instead of 192 on layer 0, no stored H_3.  Row m of
 // the padded pair space = (b, i, j) with j = m mod njp; rows with j >= n read an all-zero object row (index n_zero of Xp) and
@@ -461,7 +465,7 @@ __global__ __launch_bounds__(RR_NT) void g_chain_rr_f16s_kernel(const f16* __res
                                                                 const float* __restrict__ Vc = nullptr, int n_obj = 0,
                                                                 const float* __restrict__ Vq = nullptr, int rows_per_b = 1,
                                                                 int njp = 0, int n_zero = 0) {
-  static_assert(!RAG || (ALG0 && INJ == 0 && XG), "padded j axis: the factored first layer with the question at layer 0");
+  static_assert(!RAG || (ALG0 && XG), "padded j axis: the factored first layer (the question at layer 0 or as a per-question row)");
   static_assert(INJ >= 0 && INJ < RR_L, "the question is injected at one of the four layers");
   static_assert(INJ < RR_L - 1 || (XG && ALG0), "the last layer's question row is overwritten behind the pair-sum barrier of the tail");
   static_assert(!H8 || STORE, "e4m3 copies of H_0..2 (a stored H_3 stays bf16: the pair sum reads it)");
@@ -525,6 +529,10 @@ __global__ __launch_bounds__(RR_NT) void g_chain_rr_f16s_kernel(const f16* __res
   f32x4 vcreg = {0.f, 0.f, 0.f, 0.f};
   f32x4 vqreg = {0.f, 0.f, 0.f, 0.f};
   auto vq_load = [&](int tile_) -> f32x4 {
+    if constexpr (RAG) {                                               // wave 1: the row of the tile's LAST question (RAG && INJ, below)
+      const long r = (long)tile_ * RR_TM + (w == 1 ? RR_TM - 1 : 0);
+      return *reinterpret_cast<const f32x4*>(Vq + (r / rows_per_b) * RR_G + lane * 4);
+    }
     return *reinterpret_cast<const f32x4*>(Vq + (long)(((long)tile_ * RR_TM) / rows_per_b) * RR_G + lane * 4);
   };
 
@@ -550,7 +558,9 @@ __global__ __launch_bounds__(RR_NT) void g_chain_rr_f16s_kernel(const f16* __res
   if (t < RR_G) {
 #pragma unroll
     for (int l = 0; l < RR_L; ++l)
-      bias_s[l * RR_G + t] = (INJ > 0 && l == INJ) ? Vq[(long)(((long)tile * RR_TM) / rows_per_b) * RR_G + t] : a.bias[l][t];
+      bias_s[l * RR_G + t] = (INJ > 0 && l == INJ)            ? Vq[(long)(((long)tile * RR_TM) / rows_per_b) * RR_G + t]
+                             : (RAG && INJ > 0 && l == 0) ? Vq[(long)(((long)tile * RR_TM + RR_TM - 1) / rows_per_b) * RR_G + t]
+                                                          : a.bias[l][t];
   }
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   __syncthreads();
@@ -576,6 +586,20 @@ __global__ __launch_bounds__(RR_NT) void g_chain_rr_f16s_kernel(const f16* __res
     float xs[8];
 #pragma unroll
     for (int i = 0; i < 8; ++i) xs[i] = 0.f;
+    // RAG && INJ: a tile may hold rows of two questions, split at a wave boundary (rows per question = n * njp, a multiple of 128):
+    // the waves of the second one read its row of layer INJ from the slot of layer 0 (ALG0: layer 0 reads vc_s, never that slot).
+    // One SGPR per tile: the slot's offset for this wave.
+    unsigned inj_off = INJ * RR_G;
+    if constexpr (RAG && INJ > 0) {
+      const int r0 = tile * RR_TM;
+      inj_off = (r0 + RR_WR * w) / rows_per_b != r0 / rows_per_b ? 0u : (unsigned)(INJ * RR_G);
+      asm volatile("" : "+s"(inj_off));
+    }
+    auto bias_row = [&](int l) -> const float* {
+      if constexpr (RAG && INJ > 0)
+        if (l == INJ) return bias_s + inj_off;
+      return bias_s + l * RR_G;
+    };
     // RAG: valid rows of this wave = the first nv (a multiple of 4; 32 for all but a group's last wave).  Lane masks: swapped
     // layers 0..2 have lane = row (both lane halves), the last layer accumulator group j' of lane half hh = rows 8 j' + 4 hh + r
     u64 vm012 = ~0ull, vm3[4] = {~0ull, ~0ull, ~0ull, ~0ull};
@@ -594,7 +618,7 @@ __global__ __launch_bounds__(RR_NT) void g_chain_rr_f16s_kernel(const f16* __res
     auto bias_read = [&](int l, int ob) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float* src = (ALG0 && l == 0) ? vc_s : bias_s + l * RR_G;
+        const float* src = (ALG0 && l == 0) ? vc_s : bias_row(l);
         const f32x4 b = *reinterpret_cast<const f32x4*>(src + 32 * ob + 8 * j + 4 * h);
 #pragma unroll
         for (int r = 0; r < 4; ++r) cinit[4 * j + r] = b[r];
@@ -749,7 +773,7 @@ __global__ __launch_bounds__(RR_NT) void g_chain_rr_f16s_kernel(const f16* __res
       constexpr int dl = (didx >> 3) & 3, dob = didx & 7;
       constexpr int slot = ob & 3, nslot = (ob + 1) & 3, dslot = (ob + F_LA) & 3;
       if (l < RR_L - 1 && !(ABL & 1)) bias_read(l, ob);
-      if (has_prev && pl == RR_L - 1) b3 = bias_s[pl * RR_G + 32 * pob + n];
+      if (has_prev && pl == RR_L - 1) b3 = bias_row(pl)[32 * pob + n];
       if (ABL & 4) {
       } else if (Vm::younger(sidx, true) != Vm::younger(sidx, false)) {
         if (first) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(Vm::younger(sidx, true)) : "memory");
@@ -832,7 +856,7 @@ __global__ __launch_bounds__(RR_NT) void g_chain_rr_f16s_kernel(const f16* __res
 #pragma unroll
         for (int q = 0; q < 2; ++q) co_store(RR_L - 1, 6, q);
       }
-      b3 = bias_s[(RR_L - 1) * RR_G + 32 * 7 + n];
+      b3 = bias_row(RR_L - 1)[32 * 7 + n];
       if constexpr (GATE) {                                             // (constant indices: a loop here keeps the operand arrays out of registers)
         h2_stage(7, 0, actB[14][0], actB[14][1]);
         h2_stage(7, 1, actB[14][2], actB[14][3]);
@@ -906,6 +930,13 @@ __global__ __launch_bounds__(RR_NT) void g_chain_rr_f16s_kernel(const f16* __res
           if constexpr (Vm::VQ_TAIL) vqreg = vq_load(tnext);
           *reinterpret_cast<f32x4*>(bias_s + INJ * RR_G + lane * 4) = vqreg;
           asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        }
+        if constexpr (RAG) {
+          if (w == 1) {                                                 // (the row of the next tile's last question, same ordering)
+            if constexpr (Vm::VQ_TAIL) vqreg = vq_load(tnext);
+            *reinterpret_cast<f32x4*>(bias_s + lane * 4) = vqreg;
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+          }
         }
       }
     }
@@ -1326,10 +1357,11 @@ static int rr_num_cus() {
 extern "C" int rn_g_chain_rr_tile(void) { return RR_TM; }
 size_t rnws_rr_mask(int M) { return M > 0 ? (size_t)M * 32 : 0; }
 
-static int rr_check_inject(const char* who, const float* Vq, int inj, int n) {
+static int rr_check_inject(const char* who, const float* Vq, int inj, int n, int njp) {
   RN_CHECK_ARG(inj >= 0 && inj < RR_L, "%s: the question can be injected at layer 0 (tables) or 1, 2, 3 (a per-question bias row; got %d)", who, inj);
   RN_CHECK_ARG(inj == 0 || (Vq && ((uintptr_t)Vq % 16 == 0)), "%s: injection at layer %d needs the 16-byte aligned question rows Vq", who, inj);
-  RN_CHECK_ARG(inj == 0 || ((long)n * n) % RR_TM == 0, "%s: injection at layer %d needs n*n %% %d == 0 (n=%d)", who, inj, RR_TM, n);
+  RN_CHECK_ARG(inj == 0 || njp != n || ((long)n * n) % RR_TM == 0, "%s: injection at layer %d needs n*n %% %d == 0 (n=%d)", who, inj, RR_TM, n);
+  RN_CHECK_ARG(inj == 0 || njp == n || inj == 2, "%s: a padded j axis goes with the question at layer 0 or 2 (got %d)", who, inj);
   return 0;
 }
 
@@ -1362,16 +1394,16 @@ static int rr_f16s_args(const char* who, RRArgsF& a, const void* const* Whi, con
   return 0;
 }
 
-// The five variants of a question injected at layer INJ > 0 (whole waves per (question, i): no padded j axis): two-pass
-// inference, one-pass inference, training with e4m3 copies + gate, with e4m3 copies, with 16-bit copies.
-template <int INJ>
+// The five variants of a question injected at layer INJ > 0: two-pass inference, one-pass inference, training with e4m3 copies
+// + gate, with e4m3 copies, with 16-bit copies.  RAG: on the padded j axis (njp, the zero object row nz; rpb = n * njp).
+template <int INJ, bool RAG = false>
 static void rr_launch_inj_at(bool two, int nh, bool h8, bool gate, int grid, hipStream_t s, const f16* Xp, const RRArgsF& a, float* xg_part,
-                             int ntiles, const float* Vc, int n, const float* Vq, int rpb) {
-  if (two) g_chain_rr_f16s_kernel<4, false, false, false, true, true, INJ, false, 0, false, false, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb);
-  else if (nh == 0) g_chain_rr_f16s_kernel<4, false, false, false, true, true, INJ><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb);
-  else if (h8 && gate) g_chain_rr_f16s_kernel<4, true, false, true, true, true, INJ, true, 0, false, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb);
-  else if (h8) g_chain_rr_f16s_kernel<4, true, false, true, true, true, INJ, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb);
-  else g_chain_rr_f16s_kernel<4, true, false, true, true, true, INJ><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb);
+                             int ntiles, const float* Vc, int n, const float* Vq, int rpb, int njp = 0, int nz = 0) {
+  if (two) g_chain_rr_f16s_kernel<4, false, false, false, true, true, INJ, false, 0, RAG, false, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb, njp, nz);
+  else if (nh == 0) g_chain_rr_f16s_kernel<4, false, false, false, true, true, INJ, false, 0, RAG><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb, njp, nz);
+  else if (h8 && gate) g_chain_rr_f16s_kernel<4, true, false, true, true, true, INJ, true, 0, RAG, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb, njp, nz);
+  else if (h8) g_chain_rr_f16s_kernel<4, true, false, true, true, true, INJ, true, 0, RAG><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb, njp, nz);
+  else g_chain_rr_f16s_kernel<4, true, false, true, true, true, INJ, false, 0, RAG><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, Vq, rpb, njp, nz);
 }
 static void rr_launch_inj(int inj, bool two, int nh, bool h8, bool gate, int grid, hipStream_t s, const f16* Xp, const RRArgsF& a, float* xg_part,
                           int ntiles, const float* Vc, int n, const float* Vq, int rpb) {
@@ -1387,13 +1419,12 @@ extern "C" int rn_g_chain_fwd_rr_f16s_alg0(const void* Xp16, const float* Vc, in
   RN_CHECK_ARG(Xp16 && Vc && Whi && Wlo && bias && M > 0 && xg_part, "rn_g_chain_fwd_rr_f16s_alg0: bad pointer/size");
   RN_CHECK_ARG(!H || h_dtype == RN_BF16 || h_dtype == RN_FP8, "rn_g_chain_fwd_rr_f16s_alg0: h_dtype must be RN_BF16 or RN_FP8 (got %d)", h_dtype);
   const bool h8 = H && h_dtype == RN_FP8;
-  if (int rc = rr_check_inject("rn_g_chain_fwd_rr_f16s_alg0", Vq, inject_layer, n)) return rc;
+  if (int rc = rr_check_inject("rn_g_chain_fwd_rr_f16s_alg0", Vq, inject_layer, n, njp)) return rc;
   RN_CHECK_ARG(G == RR_G && L == RR_L, "rn_g_chain_fwd_rr_f16s_alg0: needs G == 256 and L == 4 (G=%d L=%d)", G, L);
   const bool rag = njp != n;                                          // padded j axis (see g_chain_rr_f16s_kernel, RAG)
   RN_CHECK_ARG(n > 0 && njp >= n && njp - n < RR_WR && njp % RR_WR == 0 && (!rag || n % 4 == 0) && M % ((long)n * njp) == 0 && M % RR_TM == 0,
                "rn_g_chain_fwd_rr_f16s_alg0: needs njp = 32 ceil(n / 32) (n %% 4 == 0 when padded) and M a multiple of n*njp and of %d (n=%d njp=%d M=%d)",
                RR_TM, n, njp, M);
-  RN_CHECK_ARG(!rag || inject_layer == 0, "rn_g_chain_fwd_rr_f16s_alg0: a padded j axis goes with the question at layer 0");
   RN_CHECK_ARG(((uintptr_t)Xp16 | (uintptr_t)Vc) % 16 == 0, "rn_g_chain_fwd_rr_f16s_alg0: tables must be 16-byte aligned");
   RRArgsF a;
   int nh = 0, nm = 0;
@@ -1409,13 +1440,14 @@ extern "C" int rn_g_chain_fwd_rr_f16s_alg0(const void* Xp16, const float* Vc, in
   hipStream_t s = (hipStream_t)stream;
   const int rpb = n * n;
   const f16* Xp = (const f16*)Xp16;
-  if (two) {
-    const int nz = rag ? (M / (n * njp)) * n : 0;
+  const int nz = rag ? (M / (n * njp)) * n : 0;                      // (padded: the all-zero object row behind the B * n real ones)
+  if (rag && inject_layer == 2) {
+    rr_launch_inj_at<2, true>(two, nh, h8, gate, grid, s, Xp, a, xg_part, ntiles, Vc, n, Vq, n * njp, njp, nz);
+  } else if (two) {
     if (rag) g_chain_rr_f16s_kernel<4, false, false, false, true, true, 0, false, 0, true, false, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, nullptr, 1, njp, nz);
     else if (inject_layer > 0) rr_launch_inj(inject_layer, true, 0, false, false, grid, s, Xp, a, xg_part, ntiles, Vc, n, Vq, rpb);
     else g_chain_rr_f16s_kernel<4, false, false, false, true, true, 0, false, 0, false, false, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n);
   } else if (rag) {
-    const int nz = (M / (n * njp)) * n;                               // the all-zero object row behind the B * n real ones
     if (nh == 0) g_chain_rr_f16s_kernel<4, false, false, false, true, true, 0, false, 0, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, nullptr, 1, njp, nz);
     else if (h8 && gate) g_chain_rr_f16s_kernel<4, true, false, true, true, true, 0, true, 0, true, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, nullptr, 1, njp, nz);
     else if (h8) g_chain_rr_f16s_kernel<4, true, false, true, true, true, 0, true, 0, true><<<grid, RR_NT, 0, s>>>(Xp, 64, a, xg_part, ntiles, Vc, n, nullptr, 1, njp, nz);

@@ -330,8 +330,9 @@ def chain_ok(plan: LayerPlan, B, n):
     """ONE shape predicate for the register-resident chains (rn_chain_rr.hip; the "f16s" arithmetic, what `precision: auto`
     resolves to) -- shared by the module, the autograd function and bench.py: exactly four 256-wide g layers, at most 32 features
     per object, and the question injected
-      at layer 0 (config.json original-fp): any n % 4 == 0 (n % 32 != 0 runs on the padded j axis), whole 256-row tiles;
-      at layer 1, 2 (ir-fp) or 3: whole waves per (question, i) and whole tiles per question (n % 32 == 0, n*n % 256 == 0).
+      at layer 0 (config.json original-fp) or 2 (ir-fp): any n % 4 == 0 (n % 32 != 0 runs on the padded j axis), whole 256-row
+        tiles (B * n * njp % 256 == 0); layer 2 on the padded axis: n * njp >= 4 tiles (6 x 6 grid and up);
+      at layer 1 or 3: whole waves per (question, i) and whole tiles per question (n % 32 == 0, n*n % 256 == 0).
     Everything else -- the 512-wide *-sd models, other depths, forward hooks -- runs the per-layer kernels (bf16 / fp32)."""
     if not (plan.L == 4 and all(w == 256 for w in plan.widths) and plan.k <= 32):
         return False
@@ -340,7 +341,14 @@ def chain_ok(plan: LayerPlan, B, n):
         njp = padded_j(n)
         return njp is not None and (B * n * njp) % T == 0
     inj = plan.inject
-    return 0 < inj < plan.L and plan.ktrue[inj] == 256 + plan.Q and n % 32 == 0 and (n * n) % T == 0
+    if not (0 < inj < plan.L and plan.ktrue[inj] == 256 + plan.Q):
+        return False
+    if inj == 2:                                            # (n % 32 == 0: n*n % 1024 == 0, a tile lies inside one question)
+        njp = padded_j(n)
+        # padded: a question covers at least F16S_DITHER tiles, so that the tile-dithered weight roundings average out over it
+        # (on the 2 x 2 and 4 x 4 grids they do not: 1e-3 on the log-probs) -- 6 x 6 and up
+        return njp is not None and (B * n * njp) % T == 0 and (njp == n or n * njp >= H.F16S_DITHER * T)
+    return n % 32 == 0 and (n * n) % T == 0
 
 
 f16s_ok = chain_ok
@@ -389,7 +397,7 @@ def chain_forward(x, q, plan: LayerPlan, g_b, packed, keep, inj_w=None, coord=No
     Q, G, L, R = q.shape[1], plan.widths[-1], plan.L, H.g_chain_rr_tile()
     dev = x.device
     Xp, Vc, Vq = _tables(x, q, plan, g_b, packed.w0T, inj_w, B, n, k, Q, G, coord)
-    njp = n if inj_w is not None else padded_j(n)          # pair rows per (question, i) group: padded where n % 32 != 0
+    njp = padded_j(n)                                      # pair rows per (question, i) group: padded where n % 32 != 0 (chain_ok)
     Mp = B * n * njp
     masks = Hs = None
     gate = False
@@ -402,7 +410,8 @@ def chain_forward(x, q, plan: LayerPlan, g_b, packed, keep, inj_w=None, coord=No
     assert not (two_pass and keep)
     if njp != n:
         part = torch.empty(Mp // R * 2, G, dtype=torch.float32, device=dev)      # two partial rows per tile (it may straddle questions)
-        H.g_chain_fwd_rr_f16s_alg0(Xp, Vc, n, packed.frag_hi, lo, g_b, Hs, masks, part, Mp, G, njp=njp, gate=gate)
+        H.g_chain_fwd_rr_f16s_alg0(Xp, Vc, n, packed.frag_hi, lo, g_b, Hs, masks, part, Mp, G, Vq=Vq,
+                                   inject=plan.inject if inj_w is not None else 0, njp=njp, gate=gate)
         xg = torch.empty(B, G, dtype=torch.float32, device=dev)
         H.pair_sum_tiles(part, xg, Mp, n * njp, G)
     else:
@@ -547,7 +556,7 @@ class RelationalFunction(torch.autograd.Function):
         need_grad = grad_on and any(ctx.needs_input_grad)      # under no_grad nothing is kept for a backward pass (inference kernels)
         if chain and not chain_ok(plan, B, n):
             raise RuntimeError('precision "f16s" needs the register-resident chains: four 256-wide g layers, <= 32 features per object, '
-                               'the question at layer 0 (n % 4 == 0) or 1, 2, 3 (n % 32 == 0), whole 256-row tiles (functional.chain_ok); '
+                               'the question at layer 0 or 2 (n % 4 == 0) or 1, 3 (n % 32 == 0), whole 256-row tiles (functional.chain_ok); '
                                'use "auto", "bf16" or "fp32" here')
         if coord is not None and not chain:
             raise RuntimeError("internal: a coordinate table was passed but the chain path does not apply (grid_path_ok)")
@@ -710,8 +719,8 @@ class RelationalFunction(torch.autograd.Function):
         # of the 190-us weight-gradient launch would let it
         dq_by_event = bool(inj and overlap and ctx.q_grad_async and SCHED["dq_async"])
         if inj and not dq_by_event:
-            z_ = H.wgrad_blocked_splits(M, n * n, L - 1, aligned=True)
-            if z_ > 0 and z_ % B == 0 and (M // 64) % z_ == 0 and (n * n) % (M // z_) == 0:
+            z_ = H.wgrad_blocked_splits(Mc, n * njp, L - 1, aligned=True)
+            if z_ > 0 and z_ % B == 0 and (Mc // 64) % z_ == 0 and (n * njp) % (Mc // z_) == 0:
                 rq_splits = z_
 
         def _wgrads_blocked():
@@ -799,9 +808,9 @@ class RelationalFunction(torch.autograd.Function):
                 if l == L - 1:
                     # the last layer's gradient gate_3 x dxg[question] is not stored with e4m3 copies: Rq = dxg x (the per-question
                     # counts of its gate), exact in fp32 -- the 16-bit copies take the same route
-                    H.mask_question_counts(masks[l], Rq2, M, n * n, dxg=dxg)
+                    H.mask_question_counts(masks[l], Rq2, Mc, n * njp, dxg=dxg)
                 else:
-                    H.blocked_question_sums(dZ_of[l], Rq2, M, n * n)   # (this layer's dZ is a row-blocked image)
+                    H.blocked_question_sums(dZ_of[l], Rq2, Mc, n * njp)   # (this layer's dZ is a row-blocked image; padded rows: zero)
 
             def _wgrad_question(l=l, N=N, kt=kt):                   # gW[l][:, G_prev:] = Rq^T q  (bound NOW: N, kt are layer 0's further down)
                 H.gemm_f32(Rq2, 1, N, q, Q, 1, gW[l], kt, N, Q, B, c_off=kt - Q)

@@ -332,7 +332,7 @@ def g_chain_fwd_rr_f16s_alg0(Xp16, Vc, n, Whis, Wlo0, biases, Hs, masks, xg_part
     """f16s forward chain with the factored first layer (fp16 object rows, no pair matrix).  Whis[0] / Wlo0: the hi / lo images of
     layer 0; Whis[1..3]: (dither, 65536) fp16 tile-dithered hi images each.  Wlo0 a LIST of L lo images: the two-pass inference
     arithmetic (hi + lo on every layer, Whis = the plain hi images; no Hs / masks).  njp > n: padded j axis (M = B * n * njp, Xp16
-    with a trailing zero row, two partial rows per tile in xg_part).  gate: the last layer's ReLU gate also goes into the sign bits
+    with a trailing zero row, two partial rows per tile in xg_part; inject 0 or 2).  gate: the last layer's ReLU gate also goes into the sign bits
     of the e4m3 Hs[2] image (what relu_gate_image merges from masks[3]) -- the operand of the gate job of g_wgrad_blocked."""
     L = len(Whis)
     two = isinstance(Wlo0, (list, tuple))
